@@ -7,21 +7,28 @@ the RCCL all-gather of the packed partial top-k lists and the merge kernel.  `va
 scaling: every GPU holds 1M rows, the corpus is N x 1M rows, and `value` counts 1M-row shard
 scans per second over all ranks (= queries/s at N = 1).  The STRONG-scaling line BASELINE
 configs[3] asks for (ONE 10M x 768 corpus, batch 64, rows = 10M / N per rank) is
-`extra.config4_10Mx768_sharded_batch64_k10`, printed for every N.  Inputs (corpus, queries)
-are generated in HBM and stay there; nothing crosses PCIe inside the timed region.  `value`
-is timed exactly as asked (W warm-up + K steps, nothing in front); the same region again
-behind 64 untimed scans is `extra.steady_state`, 20 scans after a 1 s idle gap `extra.cold_burst`.
+`extra.config4_10Mx768_sharded_batch64_k10`, printed for every N under --full.  Inputs (corpus,
+queries) are generated in HBM and stay there; nothing crosses PCIe inside the timed region.
+`value` is timed exactly as asked (W warm-up + K steps, nothing in front); under --full the same
+region again behind 64 untimed scans is `extra.steady_state`, 20 scans after a 1 s idle gap
+`extra.cold_burst`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the
+headline and its `roofline`.  --full adds every other leg (steady state, cold burst, the board's
+measured peaks, the other BASELINE configs, the CPU baselines and the recall checks against the
+oracle, the auto-link legs).  --dump-outputs DIR writes the last timed step's answer (rows, scores,
+distances, counts, as a caller of the path receives them) to DIR/<name>.npy.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches itself: the parent — which has not
 touched the GPU — starts `torch.distributed.run` with N ranks as a CHILD process (never an exec), relays rank 0's JSON
 line and exits with the child's code.  CX_BENCH_BACKEND=gloo lets several ranks share one GPU to rehearse it.
 
-Rank 0 prints ONE JSON line (contract in the task description) carrying `roofline`
-(live HIP-event timing of the scan kernel) and, at N = 1, `cpu_baseline` (the CPU
-restatement of the reference's brute-force path timed on this box's host cores).
+Rank 0 prints ONE JSON line carrying `roofline` (live HIP-event timing of the scan kernel)
+and, at N = 1 under --full, `cpu_baseline` (the CPU restatement of the reference's brute-force
+path timed on the host's cores).
 """
 from __future__ import annotations
 
@@ -86,6 +93,26 @@ def spawn_ranks(n: int) -> int:
     return rc if rc else (0 if line is not None else 1)
 
 
+def dump_outputs(path: str, knn) -> None:
+    """The last timed step's answer as its caller receives it, one DIR/<name>.npy each: rows (global row of each of the
+    k results, float64 holds them exactly), scores and distances (float32), counts (results per query).  Slots past a
+    query's count hold no result and are written as row -1, score / distance 0.  KB-scale: (batch x k) per array."""
+    torch.cuda.synchronize()
+    if knn.world == 1:   # single shard: the local packed list is the answer (ShardedKnn.search); rows are global at base 0
+        rows, scores, dists, counts = knn.chunk_views(knn.local)
+    else:
+        rows, scores, dists, counts = knn.out_rows, knn.out_scores, knn.out_dists, knn.out_counts
+    rows = rows.cpu().numpy().astype(np.float64)
+    scores = scores.cpu().numpy().astype(np.float32)
+    dists = dists.cpu().numpy().astype(np.float32)
+    counts = counts.cpu().numpy().astype(np.int64)
+    empty = np.arange(rows.shape[1])[None, :] >= counts[:, None]
+    rows[empty], scores[empty], dists[empty] = -1.0, 0.0, 0.0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("rows", rows), ("scores", scores), ("distances", dists), ("counts", counts.astype(np.float64))):
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,7 +131,14 @@ def main() -> None:
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the 1-thread CPU baseline leg")
     ap.add_argument("--recall-queries", type=int, default=1024,
                     help="held-out queries whose GPU answers are checked against the CPU oracle (SURVEY 8d: all 1,024; ~80 s on 16 threads)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline (steady state, cold burst, measured peaks, other configs, CPU baselines, "
+                         "recall, auto-link); the --no-* switches and --preroll act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's rows / scores / distances / counts to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -191,9 +225,8 @@ def main() -> None:
         return el, km, kn
 
     elapsed, kern_ms, kern_n = timed_region(0)
-    for i in range(args.preroll):
-        step(args.warmup + args.steps + i)
-    elapsed_ss, kern_ms_ss, kern_n_ss = timed_region(args.warmup + args.steps + args.preroll)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, knn)   # before anything else reuses the result buffers
 
     value = args.steps * B * world / elapsed
     algo_bytes = float(n) * d * 4.0  # N*d*sizeof(f32) per query per shard; norms recomputed in-scan
@@ -212,7 +245,7 @@ def main() -> None:
             break
     out = {
         # BASELINE.json's metric, verbatim; `value` is its first component (kNN queries/s), the auto-link pairs/s
-        # and recall@10 components are extra.autolink_allpairs* and extra.recall_at_k_vs_exact
+        # and recall@10 components are extra.autolink_allpairs* and extra.recall_at_k_vs_exact (--full)
         "metric": BASELINE_METRIC,
         "metric_component": "knn_queries_per_sec_1Mx768",
         "value": value,
@@ -221,6 +254,7 @@ def main() -> None:
         "steps": args.steps,
         "warmup": args.warmup,
         "preroll_untimed": 0,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -242,97 +276,101 @@ def main() -> None:
         },
     }
 
-    avg_ss = kern_ms_ss / max(1, kern_n_ss)
-    out.setdefault("extra", {})["steady_state"] = {
-        "what": f"the same {args.warmup} warm-up + {args.steps} timed steps again, behind {args.preroll} untimed scans run back to back with them "
-                "(the post-idle transient of the board has passed: profiles/r04/cold_start_probe.json)",
-        "value": args.steps * B * world / elapsed_ss, "ms_per_step": elapsed_ss / args.steps * 1e3, "preroll_untimed": args.preroll,
-        "roofline": {"bound": "hbm", "achieved": algo_bytes / (avg_ss * 1e-3) / 1e9 if avg_ss > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": (algo_bytes / (avg_ss * 1e-3) / 1e9 / HBM_PEAK_GBS) if avg_ss > 0 else 0.0, "avg_kernel_ms": avg_ss, "launches": kern_n_ss},
-    }
-    if rank == 0 and world == 1 and B == 1:
-        # what a server whose GPU idles between queries sees: 20 scans right after a 1 s gap, each timed by its own HIP events
-        time.sleep(1.0)
-        burst = []
-        for i in range(20):
-            ix.profile_read(reset=True)
-            ix.profile_enable(True)
-            step(i)
-            knn.flush()
-            torch.cuda.synchronize()
-            ix.profile_enable(False)
-            km, kn = ix.profile_read(reset=True)
-            burst.append(km / max(1, kn))
-        out["extra"]["cold_burst"] = {"what": "20 single scans right after a 1 s idle gap (host sync after each), kernel ms of each",
-                                      "kernel_ms": [round(x, 4) for x in burst], "mean_kernel_ms": float(np.mean(burst)),
-                                      "worst_kernel_ms": float(np.max(burst)),
-                                      "frac_of_hbm_peak_mean": algo_bytes / (float(np.mean(burst)) * 1e-3) / 1e9 / HBM_PEAK_GBS}
-    if rank == 0 and world == 1 and B == 1 and d % 128 == 0 and d <= 1024 and n >= 131072:
-        out["extra"]["single_query_screened"] = single_screened_leg(ix, knn, step, queries, n, d, k, args.steps, args.warmup)
-    if rank == 0 and world == 1:
-        # the box's own peaks: a plain streaming-read kernel and a register-only MFMA loop; the nominal
-        # peaks stay the contract's denominators, these say how much of what THIS board delivers the kernels reach
-        import ctypes as C
-        v = C.c_double(0)
-        if L.cx_probe_read_bw(local_rank, 3 << 30, 4, C.byref(v)) == 0 and v.value > 0:
-            out["roofline"]["measured_stream_read_GBs"] = v.value
-            out["roofline"]["frac_of_measured"] = achieved / v.value
-        w = C.c_double(0)
-        if L.cx_probe_mfma_tflops(local_rank, 50.0, C.byref(w)) == 0 and w.value > 0:
-            out.setdefault("extra", {})["measured_mfma_bf16_TFLOPs"] = w.value
-        # the same loop fed from LDS at the filter GEMM's ratio, and with that kernel's LDS-DMA traffic on top: the
-        # ceilings of its main loop on this board
-        for mode, key in ((0, "measured_mfma_bf16_lds_fed_TFLOPs"), (1, "measured_mfma_bf16_lds_fed_with_dma_TFLOPs")):
+    if args.full:
+        for i in range(args.preroll):
+            step(args.warmup + args.steps + i)
+        elapsed_ss, kern_ms_ss, kern_n_ss = timed_region(args.warmup + args.steps + args.preroll)
+        avg_ss = kern_ms_ss / max(1, kern_n_ss)
+        out.setdefault("extra", {})["steady_state"] = {
+            "what": f"the same {args.warmup} warm-up + {args.steps} timed steps again, behind {args.preroll} untimed scans run back to back with them "
+                    "(the post-idle transient of the board has passed: profiles/r04/cold_start_probe.json)",
+            "value": args.steps * B * world / elapsed_ss, "ms_per_step": elapsed_ss / args.steps * 1e3, "preroll_untimed": args.preroll,
+            "roofline": {"bound": "hbm", "achieved": algo_bytes / (avg_ss * 1e-3) / 1e9 if avg_ss > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": (algo_bytes / (avg_ss * 1e-3) / 1e9 / HBM_PEAK_GBS) if avg_ss > 0 else 0.0, "avg_kernel_ms": avg_ss, "launches": kern_n_ss},
+        }
+        if rank == 0 and world == 1 and B == 1:
+            # what a server whose GPU idles between queries sees: 20 scans right after a 1 s gap, each timed by its own HIP events
+            time.sleep(1.0)
+            burst = []
+            for i in range(20):
+                ix.profile_read(reset=True)
+                ix.profile_enable(True)
+                step(i)
+                knn.flush()
+                torch.cuda.synchronize()
+                ix.profile_enable(False)
+                km, kn = ix.profile_read(reset=True)
+                burst.append(km / max(1, kn))
+            out["extra"]["cold_burst"] = {"what": "20 single scans right after a 1 s idle gap (host sync after each), kernel ms of each",
+                                          "kernel_ms": [round(x, 4) for x in burst], "mean_kernel_ms": float(np.mean(burst)),
+                                          "worst_kernel_ms": float(np.max(burst)),
+                                          "frac_of_hbm_peak_mean": algo_bytes / (float(np.mean(burst)) * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        if rank == 0 and world == 1 and B == 1 and d % 128 == 0 and d <= 1024 and n >= 131072:
+            out["extra"]["single_query_screened"] = single_screened_leg(ix, knn, step, queries, n, d, k, args.steps, args.warmup)
+        if rank == 0 and world == 1:
+            # the box's own peaks: a plain streaming-read kernel and a register-only MFMA loop; the nominal
+            # peaks stay the contract's denominators, these say how much of what THIS board delivers the kernels reach
+            import ctypes as C
+            v = C.c_double(0)
+            if L.cx_probe_read_bw(local_rank, 3 << 30, 4, C.byref(v)) == 0 and v.value > 0:
+                out["roofline"]["measured_stream_read_GBs"] = v.value
+                out["roofline"]["frac_of_measured"] = achieved / v.value
             w = C.c_double(0)
-            if L.cx_probe_mfma_lds_tflops(local_rank, 50.0, mode, C.byref(w)) == 0 and w.value > 0:
-                out.setdefault("extra", {})[key] = w.value
-    if not args.no_config4 and B == 1:
-        # BASELINE configs[3] as stated: ONE 10M x 768 corpus row-sharded over the N ranks (strong scaling), batch 64, k=10
-        c4 = config4_sharded_leg(L, local_rank, dev, rank, world)
-        if rank == 0:
-            out.setdefault("extra", {})["config4_10Mx768_sharded_batch64_k10"] = c4
-        if rank == 0 and world == 1:   # the one-process shape over every GPU this process sees (8 on the driver's scaling node)
-            out["extra"]["config4_10Mx768_one_process_cx_sharded_batch64_k10"] = config4_one_process_leg(L, torch.cuda.device_count())
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"], extra = cpu_baseline(ix, gen, queries, n, d, k, args.cpu_seconds, args.recall_queries)
-        out.setdefault("extra", {}).update(extra)
-    del gen
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out.setdefault("extra", {})["config1_10k_x_384_k5"] = config1_leg(L, local_rank)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and (n, d) != (1_000_000, 384):
-        out.setdefault("extra", {})["config2_1M_x_384_k10"] = config2_leg(L, local_rank, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_autolink and B == 1:
-        out.setdefault("extra", {})["config4_shard_1.25Mx768_batch64_k10"] = config4_leg(L, local_rank, dev)
-        # the same shard at the reference's default embedding width (384-d, embedding.rs:43-50) and with the linker's lists
-        out["extra"]["batch64_1.25Mx384_k10"] = config4_leg(L, local_rank, dev, d=384, steps=100,
-                                                            shard_note="the reference's default width; one of 8 shards of 10M rows")
-        out["extra"]["batch128_1.25Mx384_k10"] = config4_leg(L, local_rank, dev, d=384, B=128, steps=100,
-                                                             shard_note="the reference's default width; 128 queries per call = ONE pass of two 64-query banks (row widths up to 512)")
-        out["extra"]["batch64_1.25Mx384_k100"] = config4_leg(L, local_rank, dev, d=384, k=100, steps=100,
-                                                             shard_note="the reference's default width, the linker's list length")
-        out["extra"]["batch64_1.25Mx768_k100"] = config4_leg(L, local_rank, dev, k=100, steps=60,
-                                                             shard_note="one of 8 shards of 10M rows, the linker's list length")
-    if rank == 0 and world == 1 and not args.no_autolink:
-        out.setdefault("extra", {})["autolink_allpairs"] = autolink_leg(L, local_rank, d, args.no_cpu_baseline)
-        # the same pass over the bench corpus itself: BASELINE.json's metric names "auto-link pairs/sec at 1Mx768"
-        out["extra"]["autolink_allpairs_bench_corpus"] = autolink_on_index(ix, n, d)
-        mp = out["extra"].get("measured_mfma_bf16_TFLOPs")
-        for leg in ("autolink_allpairs", "autolink_allpairs_bench_corpus"):
-            r = out["extra"][leg]["roofline"]
-            cl = out["extra"].get("measured_mfma_bf16_lds_fed_with_dma_TFLOPs")
-            if cl:
-                r["main_loop_ceiling_TFLOPs"] = cl
-                r["frac_of_main_loop_ceiling"] = r["achieved"] / cl
-            if mp:
-                r["measured_peak_TFLOPs"] = mp
-                r["frac_of_measured"] = r["achieved"] / mp
-    if rank == 0 and world == 1 and not args.no_autolink and not args.no_cpu_baseline and B == 1:
-        out["extra"]["config5_shard_6.25Mx1024_streaming_ingest"] = config5_leg(L, local_rank, dev)
-        # config 5's row width through search_batch: the batched kernel for the widths batch2 has no instance for
-        out["extra"]["config5_shard_6.25Mx1024_batch64_k10"] = config4_leg(L, local_rank, dev, n=6_250_000, d=1024, steps=10,
-                                                                           shard_note="one of 8 shards of config 5's 50M rows, f32 store")
-        out["extra"]["config5_shard_6.25Mx1024_bf16_batch64_k10"] = config4_leg(L, local_rank, dev, n=6_250_000, d=1024, steps=10, dtype="bf16",
-                                                                                shard_note="one of 8 shards of config 5's 50M rows, bf16 store")
+            if L.cx_probe_mfma_tflops(local_rank, 50.0, C.byref(w)) == 0 and w.value > 0:
+                out.setdefault("extra", {})["measured_mfma_bf16_TFLOPs"] = w.value
+            # the same loop fed from LDS at the filter GEMM's ratio, and with that kernel's LDS-DMA traffic on top: the
+            # ceilings of its main loop on this board
+            for mode, key in ((0, "measured_mfma_bf16_lds_fed_TFLOPs"), (1, "measured_mfma_bf16_lds_fed_with_dma_TFLOPs")):
+                w = C.c_double(0)
+                if L.cx_probe_mfma_lds_tflops(local_rank, 50.0, mode, C.byref(w)) == 0 and w.value > 0:
+                    out.setdefault("extra", {})[key] = w.value
+        if not args.no_config4 and B == 1:
+            # BASELINE configs[3] as stated: ONE 10M x 768 corpus row-sharded over the N ranks (strong scaling), batch 64, k=10
+            c4 = config4_sharded_leg(L, local_rank, dev, rank, world)
+            if rank == 0:
+                out.setdefault("extra", {})["config4_10Mx768_sharded_batch64_k10"] = c4
+            if rank == 0 and world == 1:   # the one-process shape over every GPU this process sees (8 on an eight-GPU node)
+                out["extra"]["config4_10Mx768_one_process_cx_sharded_batch64_k10"] = config4_one_process_leg(L, torch.cuda.device_count())
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"], extra = cpu_baseline(ix, gen, queries, n, d, k, args.cpu_seconds, args.recall_queries)
+            out.setdefault("extra", {}).update(extra)
+        del gen
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out.setdefault("extra", {})["config1_10k_x_384_k5"] = config1_leg(L, local_rank)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and (n, d) != (1_000_000, 384):
+            out.setdefault("extra", {})["config2_1M_x_384_k10"] = config2_leg(L, local_rank, dev)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_autolink and B == 1:
+            out.setdefault("extra", {})["config4_shard_1.25Mx768_batch64_k10"] = config4_leg(L, local_rank, dev)
+            # the same shard at the reference's default embedding width (384-d, embedding.rs:43-50) and with the linker's lists
+            out["extra"]["batch64_1.25Mx384_k10"] = config4_leg(L, local_rank, dev, d=384, steps=100,
+                                                                shard_note="the reference's default width; one of 8 shards of 10M rows")
+            out["extra"]["batch128_1.25Mx384_k10"] = config4_leg(L, local_rank, dev, d=384, B=128, steps=100,
+                                                                 shard_note="the reference's default width; 128 queries per call = ONE pass of two 64-query banks (row widths up to 512)")
+            out["extra"]["batch64_1.25Mx384_k100"] = config4_leg(L, local_rank, dev, d=384, k=100, steps=100,
+                                                                 shard_note="the reference's default width, the linker's list length")
+            out["extra"]["batch64_1.25Mx768_k100"] = config4_leg(L, local_rank, dev, k=100, steps=60,
+                                                                 shard_note="one of 8 shards of 10M rows, the linker's list length")
+        if rank == 0 and world == 1 and not args.no_autolink:
+            out.setdefault("extra", {})["autolink_allpairs"] = autolink_leg(L, local_rank, d, args.no_cpu_baseline)
+            # the same pass over the bench corpus itself: BASELINE.json's metric names "auto-link pairs/sec at 1Mx768"
+            out["extra"]["autolink_allpairs_bench_corpus"] = autolink_on_index(ix, n, d)
+            mp = out["extra"].get("measured_mfma_bf16_TFLOPs")
+            for leg in ("autolink_allpairs", "autolink_allpairs_bench_corpus"):
+                r = out["extra"][leg]["roofline"]
+                cl = out["extra"].get("measured_mfma_bf16_lds_fed_with_dma_TFLOPs")
+                if cl:
+                    r["main_loop_ceiling_TFLOPs"] = cl
+                    r["frac_of_main_loop_ceiling"] = r["achieved"] / cl
+                if mp:
+                    r["measured_peak_TFLOPs"] = mp
+                    r["frac_of_measured"] = r["achieved"] / mp
+        if rank == 0 and world == 1 and not args.no_autolink and not args.no_cpu_baseline and B == 1:
+            out["extra"]["config5_shard_6.25Mx1024_streaming_ingest"] = config5_leg(L, local_rank, dev)
+            # config 5's row width through search_batch: the batched kernel for the widths batch2 has no instance for
+            out["extra"]["config5_shard_6.25Mx1024_batch64_k10"] = config4_leg(L, local_rank, dev, n=6_250_000, d=1024, steps=10,
+                                                                               shard_note="one of 8 shards of config 5's 50M rows, f32 store")
+            out["extra"]["config5_shard_6.25Mx1024_bf16_batch64_k10"] = config4_leg(L, local_rank, dev, n=6_250_000, d=1024, steps=10, dtype="bf16",
+                                                                                    shard_note="one of 8 shards of config 5's 50M rows, bf16 store")
     if rank == 0:
         print(json.dumps(out), flush=True)
     ix.close()

@@ -50,7 +50,7 @@ for src, dst in (("bench.json", f"bench_{rnd}.json"), ("bench_steps20_warmup5.js
 if not os.path.exists(os.path.join(S, "cold_start_probe.json")) and os.path.exists(os.path.join(ROOT, "gpurun_out", "cold_probe.json")):
     shutil.copy(os.path.join(ROOT, "gpurun_out", "cold_probe.json"), os.path.join(D, "cold_start_probe.json"))
 traffic("knn_1Mx768_pmc_final.json", "scripts/profile_round.sh: rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --output-format csv -- "
-        "python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-autolink --no-config4", "scan_kernel<768", "knn_fetch_summary.json", "knn_write_summary.json",
+        "python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-autolink --no-config4", "scan_kernel<768", "knn_fetch_summary.json", "knn_write_summary.json",
         3_072_000_000, "scan_kernel_hbm_bytes_per_launch")
 traffic("batch64_1.25Mx768_pmc_final.json", "scripts/profile_round_b.sh: rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --output-format csv -- "
         "python3 scripts/bench_batch.py --steps 5", "batchs_kernel<768, false>", "batch_fetch_summary.json", "batch_write_summary.json",
